@@ -46,6 +46,7 @@ import os
 import statistics
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -102,6 +103,10 @@ def parse():
     ap.add_argument("--cpu-scenes", type=int, default=8, help="scenes in the bounded CPU-baseline sample")
     ap.add_argument("--no-training-leg", action="store_true",
                     help="skip the informational `training_step` object (forward + backward of the same SA layers in train() mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (every layer's new_xyz, features, "
+                         "class scores and sampled indices, rank 0) as DIR/<name>.npy in float32 / float64, at most 64 MB in "
+                         "all: larger outputs are written as a fixed, seeded sample of their elements")
     args = ap.parse_args()
     if args.config == 5:
         args.batch = 1 if args.batch is None else args.batch
@@ -561,6 +566,36 @@ def same_outputs(got, want):
     return True, ""
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_FIELDS = ("xyz", "features", "cls", "idx")
+
+
+def dump_outputs(outs, out_dir, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: the (new_xyz, new_features, cls, sampled_idx) of every layer of one pass as out_dir/layer<k>_<field>.npy.
+    Floating-point results are written as float32, indices as float64 (exact).  When the whole set would exceed `budget`
+    bytes, each array is replaced by the same fraction of its flattened elements at positions drawn from a generator seeded
+    by `seed` and the array's name (so two builds with the same shapes write the same positions) -> {name: shape written}."""
+    host = {}
+    for k, o in enumerate(outs):
+        for field, t in zip(DUMP_FIELDS, o[:4]):
+            if t is None:
+                continue
+            a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+            host[f"layer{k}_{field}"] = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    keep = 1.0 if total <= budget else budget / total
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in host.items():
+        if keep < 1.0:
+            n = max(1, int(a.size * keep))
+            rng = np.random.default_rng([seed, zlib.crc32(name.encode())])
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, n, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` outside a launcher: start the N ranks as children (torch.distributed.run, one per GPU,
     rendezvous on 127.0.0.1) -- the parent never initialises the GPU -- relay their stdout (rank 0's ONE line) and stderr,
@@ -719,6 +754,7 @@ def main():
         return rec
 
     elapsed, per_step, outs = timed(args.steps, args.warmup)
+    dumped = dump_outputs(outs, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     fps = probe.summary()
     # the pass's overlap (FPS producer beside its consumers) is only as good as the placement of its helper streams on
     # hardware queues: every rank reports whether all of them were SHOWN to run beside the pass (streams.py), AND-reduced
@@ -828,6 +864,8 @@ def main():
             line["data"] = "synthetic; REHEARSAL: all ranks share one GPU over gloo -- not a measurement"
         if checked is not None:
             line["validated"] = checked
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         # helper streams are probed for real concurrency with the pass's streams
         line["helper_streams"] = dict(_streams.stats, note="device-side probes at stream set-up; rejected = candidates that shared "
                                       "a hardware queue with the pass (HIP multiplexes streams onto GPU_MAX_HW_QUEUES queues); "

@@ -340,6 +340,26 @@ def pointnet2msg():
                         n_state=np.asarray(len(net.state_dict())))
 
 
+def backbone_state_dicts():
+    """Parameter names and shapes of the reference's IASSD_Backbone / PAGNet_Backbone / PointNet2MSG at the shipped configs,
+    and their num_point_features, as JSON (tests/test_abi_cpu.py checks the mirrors' state_dicts against it)."""
+    import json
+    import re
+    from oracle import ref_harness_stack
+    from spsnet_amd import backbones as B
+    ref_harness_stack.load_reference()   # pointnet2_backbone.py imports the stacked-op package at module level
+    out = {}
+    for cls, filename, cfg, kw in (("IASSD_Backbone", "IASSD_backbone.py", B.IASSD_KITTI_CFG, dict(num_class=3)),
+                                   ("PAGNet_Backbone", "PAGNet_backbone.py", B.SPSNET_KITTI_CFG, dict(num_class=3)),
+                                   ("PointNet2MSG", "pointnet2_backbone.py", B.POINTRCNN_KITTI_CFG, {})):
+        net = _load_backbone(filename, cls)(_attr(copy.deepcopy(cfg)), input_channels=4, **kw)
+        out[cls] = {"state_dict": {k: list(v.shape) for k, v in net.state_dict().items()},
+                    "num_point_features": int(net.num_point_features)}
+    text = re.sub(r"\[\s*([^\[\]]*?)\s*\]", lambda m: "[" + re.sub(r"\s+", " ", m.group(1)) + "]", json.dumps(out, indent=1))
+    with open(os.path.join(OUT, "backbone_state_dicts.json"), "w") as fh:
+        fh.write(text + "\n")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     U, M = ref_harness.load_reference()
@@ -349,6 +369,9 @@ def main():
         return
     if len(sys.argv) > 1 and sys.argv[1] == "pointnet2msg":
         pointnet2msg()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "backbone_state_dicts":
+        backbone_state_dicts()
         return
     ops_small(U)
     config1(M)
@@ -360,6 +383,7 @@ def main():
     surface_features()
     backbones()
     pointnet2msg()
+    backbone_state_dicts()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 

@@ -16,7 +16,9 @@ Placement rules (a "pass" = everything issued from one main stream, its ROOT):
   * a candidate stream is only handed out after the device-side probe (sps_streams_run_concurrently: a one-lane kernel on
     one stream waits, bounded by wall clock, for a word that a kernel launched on the other stream right behind it sets)
     has shown it running beside each of them; candidates that fail stay referenced (they keep their queue slot, so the
-    next one maps elsewhere).
+    next one maps elsewhere).  Candidates alternate between the requested stream priority and the other end of the range:
+    HIP keeps one pool of GPU_MAX_HW_QUEUES queues per priority, so with a small pool (2 queues: the root and the producer
+    fill it) the helpers still find queues of their own.
 A lost overlap is LOUD: a helper that could not be placed (no candidate passed, or the per-device probe budget ran out) is
 returned all the same -- results never depend on placement -- but it is recorded in `stats["unplaced"]`, `unplaced()` lists
 it, `overlap_verified()` turns False and a RuntimeWarning is raised once; bench.py prints all three on its line.
@@ -32,6 +34,8 @@ import torch
 _TRIES = int(os.environ.get("SPS_STREAM_TRIES", "12"))
 _MAX_PROBES_PER_DEVICE = int(os.environ.get("SPS_STREAM_MAX_PROBES", "160"))
 _LIMIT_US = 2000
+_HW_QUEUES = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))   # HIP's hardware queues per device and stream priority
+_QUEUES_FOR_UNPROBED = 4   # root, producer and the two scales each on a queue of their own without a probe
 _REJECTED = []          # streams that shared a queue with somebody: kept alive on purpose (bounded by the probe budget)
 _SCRATCH = {}
 _PROBES = {}            # device index -> probes spent
@@ -71,10 +75,14 @@ def new_stream_beside(device, beside: Sequence[torch.cuda.Stream], priority: int
         st._sps_unprobed = True       # handed out without a probe (set-up under capture / SPS_STREAM_PROBE=0): verifies nothing
         return st
     st = None
-    for _ in range(max(1, _TRIES)):
+    # HIP pools its hardware queues per stream priority (GPU_MAX_HW_QUEUES in each pool): once the requested priority's pool is
+    # full, a candidate of the other priority can still get a queue of its own -- the candidates alternate between the two
+    least, greatest = torch.cuda.Stream.priority_range()
+    priorities = (priority, greatest if priority != greatest else least)
+    for attempt in range(max(1, _TRIES)):
         if _PROBES.get(device.index, 0) + len(beside) > _MAX_PROBES_PER_DEVICE:
             break                       # a long-lived process with many main streams: stop probing, say so below
-        st = torch.cuda.Stream(device=device, priority=priority)
+        st = torch.cuda.Stream(device=device, priority=priorities[attempt % 2])
         if all(s.cuda_stream != st.cuda_stream and run_concurrently(s, st) for s in beside):
             return st
         _REJECTED.append(st)
@@ -114,6 +122,11 @@ def helper(device, main: torch.cuda.Stream, tag: str, exclusive: bool = False) -
     root_handle, root = _ROOT.get((device.index, main.cuda_stream), (main.cuda_stream, main))
     key = (device.index, root_handle)
     reg = _HELPERS.get(key)
+    if (reg is None or tag not in reg) and torch.cuda.is_current_stream_capturing() and _HW_QUEUES < _QUEUES_FOR_UNPROBED:
+        # a helper asked for under capture cannot be probed; with fewer hardware queues per pool than a pass keeps streams, an
+        # unprobed one shares a queue with the pass -- the captured pass issues that role on its own stream instead, in order
+        # (exact: every producer is issued before its consumers, whose bounded waits are then served at once)
+        return main
     if reg is None:
         reg = _HELPERS[key] = {}
         if not _probing_off() and os.environ.get("SPS_RESERVE_PRODUCER", "1") != "0":

@@ -113,32 +113,20 @@ def test_surface_feature_mirror_has_reference_state_dict_keys():
 
 
 def test_backbone_mirrors_have_reference_state_dict_keys():
-    """IASSD_Backbone / PAGNet_Backbone: same parameter names and shapes as the reference's classes (so checkpoints
-    load, and so scenes.fill_parameters gives both the same weights).  Needs /root/reference: build container only."""
+    """IASSD_Backbone / PAGNet_Backbone / PointNet2MSG: same parameter names and shapes as the reference's classes (so
+    checkpoints load, and so scenes.fill_parameters gives both the same weights), and the same num_point_features.  The
+    reference's side is tests/golden/backbone_state_dicts.json (oracle/gen_golden.py backbone_state_dicts)."""
     import copy
-    import pytest
-    from oracle import ref_harness
-    if not ref_harness.available():
-        pytest.skip("reference tree not present (GPU box)")
-    from oracle import gen_golden
+    import json
     from spsnet_amd import backbones as BB
-    ref_harness.load_reference()
-    for filename, cls, mine_cls, cfg in (("IASSD_backbone.py", "IASSD_Backbone", BB.IASSD_Backbone, BB.IASSD_KITTI_CFG),
-                                         ("PAGNet_backbone.py", "PAGNet_Backbone", BB.PAGNet_Backbone, BB.SPSNET_KITTI_CFG)):
-        ref = gen_golden._load_backbone(filename, cls)(gen_golden._attr(copy.deepcopy(cfg)), num_class=3, input_channels=4)
-        mine = mine_cls(copy.deepcopy(cfg), num_class=3, input_channels=4)
-        want = {k: tuple(v.shape) for k, v in ref.state_dict().items()}
-        got = {k: tuple(v.shape) for k, v in mine.state_dict().items()}
-        assert got == want
-        assert mine.num_point_features == ref.num_point_features
-    # PointRCNN's backbone (pointnet2_backbone.py imports the stacked-op package at module level: both harnesses)
-    from oracle import ref_harness_stack
-    ref_harness_stack.load_reference()
-    cfg = BB.POINTRCNN_KITTI_CFG
-    ref = gen_golden._load_backbone("pointnet2_backbone.py", "PointNet2MSG")(gen_golden._attr(copy.deepcopy(cfg)), input_channels=4)
-    mine = BB.PointNet2MSG(copy.deepcopy(cfg), input_channels=4)
-    assert {k: tuple(v.shape) for k, v in mine.state_dict().items()} == {k: tuple(v.shape) for k, v in ref.state_dict().items()}
-    assert mine.num_point_features == ref.num_point_features
+    with open(os.path.join(ROOT, "tests", "golden", "backbone_state_dicts.json")) as fh:
+        want = json.load(fh)
+    for name, mine in (("IASSD_Backbone", BB.IASSD_Backbone(copy.deepcopy(BB.IASSD_KITTI_CFG), num_class=3, input_channels=4)),
+                       ("PAGNet_Backbone", BB.PAGNet_Backbone(copy.deepcopy(BB.SPSNET_KITTI_CFG), num_class=3, input_channels=4)),
+                       ("PointNet2MSG", BB.PointNet2MSG(copy.deepcopy(BB.POINTRCNN_KITTI_CFG), input_channels=4))):
+        got = {k: list(v.shape) for k, v in mine.state_dict().items()}
+        assert got == want[name]["state_dict"], name
+        assert mine.num_point_features == want[name]["num_point_features"], name
 
 
 def test_fill_parameters_is_deterministic_and_name_keyed():
