@@ -293,9 +293,10 @@ __global__ __launch_bounds__(PF_THREADS) void fps_pruned_kernel(
     //   (b) t_(k) > BOUND of every earlier e_(i)'s wave (which includes e_(i)'s own distance after it was picked)
     // because running distances only ever decrease: after the earlier picks e_(k) is unchanged while every other
     // point is still <= its old value, which was below e_(k)'s key -- (b) covers the points that were not
-    // published.  The round accepts the longest such prefix (L >= 1: e_(1) is the plain FPS pick), then applies the L
-    // updates (min is order-independent).  Rejecting is always safe, so every comparison that involves a NaN
-    // rejects.  One barrier and one LDS exchange per ROUND instead of per sample.
+    // published.  The part of BOUND that covers the rest of e_(i)'s own bucket is taken after e_(i)'s update of
+    // those points, which sequential FPS has applied by the time it compares e_(k) with them.  The round accepts the
+    // longest such prefix (L >= 1: e_(1) is the plain FPS pick), then applies the L updates (min is order-independent).
+    // Rejecting is always safe, so every comparison that involves a NaN rejects.  One barrier and one LDS exchange per ROUND instead of per sample.
     constexpr int IMIN = (int)0x80000000;
     int crec = 0;  // the wave's two records as lanes 0..11 publish them: lane 2f+r = field f {dist, keylo, x, y, z, bound} of record r
     bool cand_stale = true;
@@ -382,7 +383,18 @@ __global__ __launch_bounds__(PF_THREADS) void fps_pruned_kernel(
             const int wl2 = best_bucket(mine && lane != wl1, v2);
             // the best of the other buckets, and the runner-up inside each of the two buckets: one interleaved reduction
             const int hl1 = __builtin_amdgcn_readlane(bhold, wl1), hl2 = __builtin_amdgcn_readlane(bhold, wl2);
-            const float tw1 = t[wl1], tw2 = t[wl2];
+            // the rest of each bucket as its own record's update will leave it: once record r has been picked, every
+            // other point of its bucket is at most fmin(sqdist(point, record r), its running distance) -- exactly what
+            // the apply computes for it, and later picks only lower it further.  The bucket's points lie close to its
+            // maximum, so this bound sits well below the bucket's plain runner-up and hides fewer of the next records.
+            auto after_own = [&](int wl) -> float {
+                const float cx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bpx), wl));
+                const float cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bpy), wl));
+                const float cz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bpz), wl));
+                const float xs = x[wl], ys = y[wl], zs = z[wl];
+                return fmin_raw(sqdist(xs, ys, zs, cx, cy, cz), t[wl]);
+            };
+            const float tw1 = after_own(wl1), tw2 = after_own(wl2);
             int v3 = (mine && lane != wl1 && lane != wl2) ? bmax : IMIN;
             int t21 = lane != hl1 ? __float_as_int(tw1) : IMIN;
             int t22 = lane != hl2 ? __float_as_int(tw2) : IMIN;
@@ -405,8 +417,8 @@ __global__ __launch_bounds__(PF_THREADS) void fps_pruned_kernel(
                 put_lane<8 + R>(crec, pz);
                 put_lane<10 + R>(crec, bound);
             };
-            // once record 1 is gone: the rest of its bucket (everything else is still below record 2);
-            // once record 2 is gone too: the rest of its bucket and all other buckets
+            // once record 1 is gone: the rest of its bucket after record 1's update (everything else is still below
+            // record 2); once record 2 is gone too: the rest of its bucket after record 2's update, and all other buckets
             record(wl1, v1, t21, std::integral_constant<int, 0>{});
             record(wl2, v2, imax(t22, v3), std::integral_constant<int, 1>{});
             cand_slot = wl1;
